@@ -16,18 +16,24 @@ environment the script starts ``torch.distributed.run --nproc-per-node N`` on it
 as a CHILD process (before anything touches the GPU; no exec) and exits with its
 code, so one command measures N ranks on N GPUs (RCCL over xGMI); under
 torchrun (the driver's N > 1 launch) it is one of the ranks. The JSON carries the
-evidence that N distinct devices took part (``device_ids``), the RCCL version,
-the small-all-reduce path the start-up race chose with both timings, the
-per-step all-reduce time measured in isolation after the timed region, and the
-held-out accuracy of the trained model (a correctness witness: a fast but wrong
-gradient kernel cannot post a number).
+evidence that N distinct devices took part (``device_ids``), the RCCL version and
+the small-all-reduce path the start-up race chose with both timings.
 
-After the headline (untimed by it, at every N on GPUs: ``--secondary``), the same JSON
-line carries BASELINE configs #3-#5 under ``secondary``: BMUF and EASGD on the headline's
-data (exact sampled-row counts, held-out witnesses), the k-means reference job at 100M x
-128, k = 1024 (also on overlapping clusters) and the PageRank reference job at R-MAT scale
-26 (adjacency build + 10 iterations), each with its witness (dalgo/apps/jobs.py). A
-failed secondary witness makes the exit code non-zero.
+A plain run does only what the headline figure needs: data generation, warmup, the
+launch-form calibration (it decides which form the timed steps run), the K timed steps,
+the result line. ``--dump-outputs DIR`` also writes what the timed steps computed (the
+model after the last timed step, the exact sampled-row count) as ``DIR/<name>.npy``; the
+inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds everything else, after the timed region and untimed by it: the per-step
+all-reduce time measured in isolation, the held-out accuracy of the trained model (a
+correctness witness: a fast but wrong gradient kernel fails the run), and, at every N on
+GPUs (``--secondary``), BASELINE configs #3-#5 under a ``secondary`` key of the same JSON
+line: BMUF and EASGD on the headline's data (exact sampled-row counts, held-out
+witnesses), the k-means reference job at 100M x 128, k = 1024 (also on overlapping
+clusters) and the PageRank reference job at R-MAT scale 26 (adjacency build + 10
+iterations), each with its witness (dalgo/apps/jobs.py). A failed witness, headline or
+secondary, makes the exit code non-zero.
 """
 from __future__ import annotations
 
@@ -56,8 +62,15 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="collective backend (default: nccl = RCCL on GPU, gloo on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not "
+                         "need: the all-reduce probe, the held-out witness (--eval) and the "
+                         "secondary configs (--secondary); without it those options are idle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed steps computed (model after the last timed "
+                         "step, sampled-row count) as DIR/<name>.npy")
     ap.add_argument("--eval", dest="eval", action="store_true", default=True,
-                    help="held-out accuracy after the timed region (default on)")
+                    help="with --full: held-out accuracy after the timed region (default on)")
     ap.add_argument("--no-eval", dest="eval", action="store_false")
     ap.add_argument("--n-test", type=int, default=100_000, help="held-out rows for the witness")
     ap.add_argument("--witness-steps", type=int, default=1500,
@@ -77,7 +90,7 @@ def parse(argv=None):
     ap.add_argument("--pg-timeout-s", type=float, default=120.0,
                     help="process-group timeout: an RCCL collective stuck longer aborts the rank")
     ap.add_argument("--secondary", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline, the BMUF / EASGD, k-means and PageRank jobs "
+                    help="with --full: after the headline, the BMUF / EASGD, k-means and PageRank jobs "
                          "(BASELINE configs #3-#5) under a 'secondary' key of the same JSON "
                          "line, at every N; auto = on for GPU runs")
     ap.add_argument("--secondary-budget-s", type=float, default=240.0,
@@ -96,7 +109,10 @@ def parse(argv=None):
     ap.add_argument("--deadline-s", type=float, default=540.0,
                     help="wall-clock deadline per rank: past it the rank prints its stacks and "
                          "exits 124 (a hang becomes a fast, rank-tagged failure); 0 = off")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.full:   # a plain run: the headline alone
+        a.eval, a.secondary = False, "off"
+    return a
 
 
 def calibrate_launch(model, rt, a) -> dict:
@@ -260,12 +276,33 @@ def allreduce_probe(model, rt, iters: int = 100) -> float | None:
     return float(el.item()) / iters * 1e6
 
 
+def dump_outputs(path: str, model, rt, samples: float) -> None:
+    """What a caller of the timed steps receives, as ``path/<name>.npy`` (rank 0 writes):
+    the model after the last timed step (f32, replicated on every rank), the exact count
+    of rows the timed steps sampled (f64) and, for MA / BMUF / EASGD, rank 0's local
+    models. A few KB at the benchmark's sizes."""
+    import numpy as np
+    arrays = {"w": model.weights(),   # (completes a deferred EASGD centre update: every rank)
+              "samples_counted": torch.tensor([samples], dtype=torch.float64)}
+    if hasattr(model, "W"):
+        arrays["locals_rank0"] = model.W
+    rt.synchronize()
+    if not rt.is_main:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
 def run_lr(a, rt, data, layout, algo: str, steps: int, warmup: int, witness_steps: int,
-           calibrate: bool) -> dict:
+           calibrate: bool, dump_dir: str | None = None) -> dict:
     """One LR-family configuration on the shared data: warmup, optional launch-form
     calibration, EXACTLY ``steps`` timed training steps (barrier + synchronize on both
-    sides, MAX over ranks; sampled rows counted on the device), then the held-out witness
-    (untimed: training continues to ``witness_steps`` total steps)."""
+    sides, MAX over ranks; sampled rows counted on the device), the outputs of those steps
+    to ``dump_dir`` if given, then (``--full``) the held-out witness (untimed: training
+    continues to ``witness_steps`` total steps)."""
     from dalgo.models.localsgd import ParallelSGD, SGDConfig
     from dalgo.parallel import comm
     W = rt.world_size
@@ -329,7 +366,10 @@ def run_lr(a, rt, data, layout, algo: str, steps: int, warmup: int, witness_step
            "device_wait_fallback": fell_back}
     if cal:
         out["launch_calibration_ms_per_step"] = cal
-    out["allreduce_us_per_step"] = allreduce_probe(model, rt) if algo in ("ssgd", "gd") else None
+    if dump_dir is not None:
+        dump_outputs(dump_dir, model, rt, samples)
+    out["allreduce_us_per_step"] = (allreduce_probe(model, rt)
+                                    if a.full and algo in ("ssgd", "gd") else None)
     if a.eval:
         # correctness witness (untimed): train on to witness_steps and score the held-out
         # split against the planted model, whose own accuracy / log-loss on that split are
@@ -472,7 +512,8 @@ def main(argv=None):
     rt.synchronize()
     gen_s = time.time() - t0
     head = run_lr(a, rt, data, layout, a.algo, a.steps, a.warmup, a.witness_steps,
-                  calibrate=a.launch == "auto")
+                  calibrate=a.launch == "auto",
+                  dump_dir=os.path.abspath(a.dump_outputs) if a.dump_outputs else None)
     sec_on = a.secondary == "on" or (a.secondary == "auto" and rt.device.type == "cuda")
     sec = run_secondary(a, rt, data, layout) if sec_on else None
     value = head["value"]
@@ -499,6 +540,7 @@ def main(argv=None):
             "per_gpu_samples_per_s": value / W,
             "effective_hbm_GBps_per_gpu": value / W * a.dim * (2 if dtype == torch.bfloat16 else 4) / 1e9,
             "datagen_s": gen_s,
+            "full": a.full,
         }
         if "launch_calibration_ms_per_step" in head:
             out["launch_calibration_ms_per_step"] = head["launch_calibration_ms_per_step"]

@@ -4,9 +4,9 @@
 set -e
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-for w in "ssgd:bench.py --steps 20 --warmup 5" \
+for w in "ssgd:bench.py --full --steps 20 --warmup 5" \
          "kmeans:bench/kmeans_bench.py --rows 20000000 --steps 3" \
-         "ssgd_small:bench.py --steps 200 --warmup 20 --rows 1250000" \
+         "ssgd_small:bench.py --full --steps 200 --warmup 20 --rows 1250000" \
          "pagerank:bench/pagerank_bench.py --steps 5" \
          "misc:bench/misc_bench.py"; do
   name=${w%%:*}; cmd=${w#*:}

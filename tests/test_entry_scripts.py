@@ -191,11 +191,47 @@ def test_bench_cpu_contract():
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run carries the headline alone (no witness, no all-reduce probe, no
+    secondaries) and --dump-outputs writes the model after the last timed step and the
+    sampled-row count; the same arguments give the same outputs in a second process."""
+    import numpy as np
+    args = ["bench.py", "--device", "cpu", "--rows", "20000", "--dim", "64", "--steps", "3",
+            "--warmup", "1", "--dtype", "f32"]
+    outs = []
+    for run in ("a", "b"):
+        out = _run(args + ["--dump-outputs", str(tmp_path / run)])
+        d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+        assert "correctness_witness" not in d and "secondary" not in d
+        assert d["allreduce_us_per_step"] is None
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["samples_counted.npy", "w.npy"]
+        w = np.load(tmp_path / run / "w.npy")
+        n = np.load(tmp_path / run / "samples_counted.npy")
+        assert w.dtype == np.float32 and w.shape == (65,) and np.isfinite(w).all()
+        assert n.dtype == np.float64 and int(n[0]) == d["samples_counted"] > 0
+        outs.append((w, n))
+    # the CPU path sums in a fixed order: bitwise equal
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+    # the dumped model is the one 1 + 3 training steps give
+    import torch
+    from dalgo.data.datasets import synthetic_logistic
+    from dalgo.models.localsgd import ParallelSGD, SGDConfig
+    from dalgo.parallel import runtime
+    from dalgo.parallel.sharding import make_layout
+    rt = runtime.init(device="cpu")
+    data = synthetic_logistic(20000, 64, device=rt.device, dtype=torch.float32)
+    m = ParallelSGD(SGDConfig(algo="ssgd", n_workers=1, eval_every=0), data,
+                    make_layout(20000, 1, 1, 0, spark_compatible=False), rt)
+    m.run_steps(4)
+    assert np.allclose(m.weights().numpy(), outs[0][0], rtol=1e-6, atol=1e-7)
+
+
 def test_bench_self_launches_n_ranks():
     """python bench.py --gpus 2 with no launcher environment starts 2 ranks itself
     (torchrun child process) and reports dp2 with both ranks' device records."""
     out = _run(["bench.py", "--gpus", "2", "--device", "cpu", "--backend", "gloo", "--rows", "20000",
-                "--dim", "64", "--steps", "3", "--warmup", "1", "--dtype", "f32", "--n-test", "5000"],
+                "--dim", "64", "--steps", "3", "--warmup", "1", "--dtype", "f32", "--n-test", "5000", "--full"],
                timeout=600)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -299,7 +335,7 @@ def test_bench_recovers_from_device_wait_failure():
     falls back to the plain per-step form, re-runs warmup + timed steps and the bench
     still reports a valid (witness-checked) number, flagged in the JSON."""
     out = _run(["bench.py", "--gpus", "2", "--device", "cpu", "--backend", "gloo", "--rows", "20000",
-                "--dim", "64", "--steps", "3", "--warmup", "1", "--dtype", "f32", "--n-test", "5000"],
+                "--dim", "64", "--steps", "3", "--warmup", "1", "--dtype", "f32", "--n-test", "5000", "--full"],
                env_extra={"DALGO_TEST_FORCE_DEVICE_ERROR": "1"}, timeout=600)
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     assert d["device_wait_fallback"] is True and d["n_gpus"] == 2
@@ -309,7 +345,7 @@ def test_bench_recovers_from_device_wait_failure():
     # clean run exactly (same sample count, same trained model)
     clean = _run(["bench.py", "--gpus", "2", "--device", "cpu", "--backend", "gloo", "--rows",
                   "20000", "--dim", "64", "--steps", "3", "--warmup", "1", "--dtype", "f32",
-                  "--n-test", "5000"], timeout=600)
+                  "--n-test", "5000", "--full"], timeout=600)
     c = json.loads([l for l in clean.splitlines() if l.startswith("{")][0])
     assert c["device_wait_fallback"] is False
     assert d["config"]["global_batch"] == c["config"]["global_batch"]

@@ -86,7 +86,8 @@ def test_bench_secondary_two_ranks(cuda):
     BMUF / EASGD, both k-means jobs and the sharded PageRank job, every witness passing."""
     out = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--rows", "200000",
                      "--steps", "5", "--warmup", "2", "--secondary-steps", "5", "--secondary-warmup", "2",
-                     "--km-rows", "2000000", "--pr-scale", "16", "--km-pool-gb", "4", "--pr-pool-gb", "4"])
+                     "--km-rows", "2000000", "--pr-scale", "16", "--km-pool-gb", "4", "--pr-pool-gb", "4",
+                     "--full"])
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     sec = d["secondary"]
     assert set(sec) == {"bmuf", "easgd", "kmeans", "kmeans_overlapping", "pagerank"}, sec.keys()
@@ -104,7 +105,7 @@ def test_bench_two_ranks_shared_gpu(cuda):
     rank sees shared_device, K11 is never built even when forced (so no persistent /
     one-kernel form either) and the bench reports the process group."""
     out = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--rows", "200000",
-                     "--steps", "5", "--warmup", "2"], env_extra={"DALGO_XGMI": "1"})
+                     "--steps", "5", "--warmup", "2", "--full"], env_extra={"DALGO_XGMI": "1"})
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
