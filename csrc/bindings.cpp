@@ -588,36 +588,83 @@ void kmeans_qsum(const Tensor& assign, const Tensor& xh, int64_t k, Tensor Q) {
                   "kmeans_qsum");
 }
 
-// K2 (variant 52) over the rows idx[0, m) only
-void kmeans_assign_idx(const Tensor& X, const Tensor& Cq, const Tensor& hn,
-                       const std::optional<Tensor>& idx, int64_t m, Tensor assign,
-                       at::TensorList cand,
-                       const std::optional<Tensor>& mind, const std::optional<Tensor>& mind2,
-                       const std::optional<Tensor>& xh, const std::optional<Tensor>& xmax,
-                       const std::optional<Tensor>& m_dev, const std::optional<Tensor>& a_prev,
-                       const std::optional<Tensor>& tol, const std::optional<Tensor>& ul,
-                       const std::optional<Tensor>& changed,
-                       const std::optional<Tensor>& n_changed, const std::optional<Tensor>& chg_new,
-                       const std::optional<Tensor>& chg_old, int64_t cand_extend,
-                       const std::optional<Tensor>& acl) {
+// K2 over the rows idx[0, m) only (rows 0 .. m without idx): one op per form of
+// kmeans.hip (dalgo_kmeans_assign_rows / _filtered / _cand). What the three share (returns
+// idx's pointer; DP and kpad are Cq's sizes):
+static const int32_t* km_rows_check(const char* op, const Tensor& X, const Tensor& Cq, const Tensor& hn,
+                                    const std::optional<Tensor>& idx, int64_t m, const Tensor& assign) {
   TORCH_CHECK(Cq.dim() == 2 && Cq.is_contiguous() && Cq.scalar_type() == at::kBFloat16, "Cq bf16");
   const int DP = (int)Cq.size(1);
-  TORCH_CHECK(DP == 64 || DP == 128, "kmeans_assign_idx: DP 64 or 128");
+  TORCH_CHECK(DP == 64 || DP == 128, op, ": DP 64 or 128");
   check_points(X, DP);
-  TORCH_CHECK(X.scalar_type() == at::kBFloat16, "kmeans_assign_idx: bf16 points");
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16, op, ": bf16 points");
   const int64_t kpad = Cq.size(0);
-  TORCH_CHECK(kpad % 128 == 0, "kmeans_assign_idx: kpad % 128");
+  TORCH_CHECK(kpad % 128 == 0, op, ": kpad % 128");
   check_f32(hn, "hn");
   const int32_t* ip = nullptr;
   if (idx.has_value()) {
     check_i32(*idx, "idx");
-    TORCH_CHECK(m >= 0 && m <= idx->numel(), "kmeans_assign_idx: m");
+    TORCH_CHECK(m >= 0 && m <= idx->numel(), op, ": m");
     ip = idx->data_ptr<int32_t>();
   } else {
-    TORCH_CHECK(m >= 0 && m <= X.size(0), "kmeans_assign_idx: m <= n");
+    TORCH_CHECK(m >= 0 && m <= X.size(0), op, ": m <= n");
   }
   check_i32(assign, "assign");
   TORCH_CHECK(assign.numel() >= X.size(0), "assign [n]");
+  return ip;
+}
+
+// The filtered iteration's epilogue block: rows = *m_dev (device), m = its upper bound.
+// Previous clusters: a_prev[row], acl[p] (the filter's list order), the candidate form's
+// tiles, or (none given, dense form) assign itself.
+static DalgoKmPost km_post_check(const char* op, const Tensor& X, const int32_t* ip, int64_t m,
+                                 const Tensor& m_dev, const Tensor& tol, const Tensor& ul,
+                                 const Tensor& changed, const Tensor& n_changed,
+                                 const std::optional<Tensor>& a_prev, const std::optional<Tensor>& acl,
+                                 const std::optional<Tensor>& chg_new,
+                                 const std::optional<Tensor>& chg_old) {
+  DalgoKmPost post{};
+  check_dev(m_dev, "m_dev");
+  TORCH_CHECK(m_dev.scalar_type() == at::kLong && m_dev.numel() >= 1, "m_dev int64[1]");
+  if (a_prev.has_value()) {
+    check_i32(*a_prev, "a_prev");
+    TORCH_CHECK(a_prev->numel() >= X.size(0), "a_prev [n]");
+    post.a_prev = a_prev->data_ptr<int32_t>();
+  }
+  if (acl.has_value()) {
+    check_i32(*acl, "acl");
+    TORCH_CHECK(ip != nullptr && acl->numel() >= m, op, ": acl [m] with idx");
+    post.acl = acl->data_ptr<int32_t>();
+  }
+  check_i32(changed, "changed");
+  TORCH_CHECK(chg_new.has_value() == chg_old.has_value(), "chg_new and chg_old together");
+  if (chg_new.has_value()) {
+    check_i32(*chg_new, "chg_new");
+    check_i32(*chg_old, "chg_old");
+    TORCH_CHECK(chg_new->numel() >= changed.numel() && chg_old->numel() >= changed.numel(),
+                "chg_new / chg_old [cap]");
+    post.chg_new = chg_new->data_ptr<int32_t>();
+    post.chg_old = chg_old->data_ptr<int32_t>();
+  }
+  check_f32(tol, "tol");
+  TORCH_CHECK(n_changed.scalar_type() == at::kLong && n_changed.numel() >= 1, "n_changed int64[1]");
+  check_dev(n_changed, "n_changed");
+  post.mcount = reinterpret_cast<const unsigned long long*>(m_dev.data_ptr<int64_t>());
+  post.tol = tol.data_ptr<float>();
+  check_ul(ul, X.size(0), op);
+  post.ul = ul.data_ptr<float>();
+  post.changed = changed.data_ptr<int32_t>();
+  post.n_changed = reinterpret_cast<unsigned long long*>(n_changed.data_ptr<int64_t>());
+  post.cap = changed.numel();
+  return post;
+}
+
+// the pass with a host row count (mind2: the top-2 form; xh / xmax: 0.5|x|^2 and its max)
+void kmeans_assign_rows(const Tensor& X, const Tensor& Cq, const Tensor& hn,
+                        const std::optional<Tensor>& idx, int64_t m, Tensor assign,
+                        const std::optional<Tensor>& mind, const std::optional<Tensor>& mind2,
+                        const std::optional<Tensor>& xh, const std::optional<Tensor>& xmax) {
+  const int32_t* ip = km_rows_check("kmeans_assign_rows", X, Cq, hn, idx, m, assign);
   auto f32n = [&](const std::optional<Tensor>& t, const char* nm) -> float* {
     if (!t.has_value()) return nullptr;
     check_f32(*t, nm);
@@ -633,92 +680,85 @@ void kmeans_assign_idx(const Tensor& X, const Tensor& Cq, const Tensor& hn,
     TORCH_CHECK(xmax->scalar_type() == at::kInt && xmax->numel() >= 1, "xmax int32[1] (float bits)");
     xmp = reinterpret_cast<unsigned*>(xmax->data_ptr<int32_t>());
   }
-  DalgoKmPost post{};
-  const DalgoKmPost* pp = nullptr;
-  if (m_dev.has_value()) {   // filtered iteration: rows = *m_dev (device), m = its upper bound
-    // previous clusters: a_prev[row], acl[p] (the filter's list order), the candidate
-    // form's tiles, or (none given, dense form) assign itself
-    TORCH_CHECK(tol.has_value() && ul.has_value() &&
-                    changed.has_value() && n_changed.has_value(),
-                "kmeans_assign_idx: the device-count form needs a_prev, tol, ul, changed, n_changed");
-    check_dev(*m_dev, "m_dev");
-    TORCH_CHECK(m_dev->scalar_type() == at::kLong && m_dev->numel() >= 1, "m_dev int64[1]");
-    if (a_prev.has_value()) {
-      check_i32(*a_prev, "a_prev");
-      TORCH_CHECK(a_prev->numel() >= X.size(0), "a_prev [n]");
-      post.a_prev = a_prev->data_ptr<int32_t>();
-    }
-    if (acl.has_value()) {
-      check_i32(*acl, "acl");
-      TORCH_CHECK(ip != nullptr && acl->numel() >= m, "kmeans_assign_idx: acl [m] with idx");
-      post.acl = acl->data_ptr<int32_t>();
-    }
-    check_i32(*changed, "changed");
-    TORCH_CHECK(chg_new.has_value() == chg_old.has_value(), "chg_new and chg_old together");
-    if (chg_new.has_value()) {
-      check_i32(*chg_new, "chg_new");
-      check_i32(*chg_old, "chg_old");
-      TORCH_CHECK(chg_new->numel() >= changed->numel() && chg_old->numel() >= changed->numel(),
-                  "chg_new / chg_old [cap]");
-      post.chg_new = chg_new->data_ptr<int32_t>();
-      post.chg_old = chg_old->data_ptr<int32_t>();
-    }
-    check_f32(*tol, "tol");
-    TORCH_CHECK(n_changed->scalar_type() == at::kLong && n_changed->numel() >= 1, "n_changed int64[1]");
-    check_dev(*n_changed, "n_changed");
-    post.mcount = reinterpret_cast<const unsigned long long*>(m_dev->data_ptr<int64_t>());
-    post.tol = tol->data_ptr<float>();
-    check_ul(*ul, X.size(0), "kmeans_assign_idx");
-    post.ul = ul->data_ptr<float>();
-    post.changed = changed->data_ptr<int32_t>();
-    post.n_changed = reinterpret_cast<unsigned long long*>(n_changed->data_ptr<int64_t>());
-    post.cap = changed->numel();
-    pp = &post;
-  } else {
-    TORCH_CHECK(md != nullptr, "kmeans_assign_idx: mind");
-  }
-  // candidate-pruned form: [tiles int32 [T, 4], n_tiles, hnb, nb, nd] (+ [ndb, dnb]: drift-aware)
+  TORCH_CHECK(md != nullptr, "kmeans_assign_rows: mind");
+  DeviceGuard guard(X.device());
+  DALGO_CHECK_HIP(dalgo_kmeans_assign_rows(X.data_ptr(), m, X.stride(0), (int)Cq.size(1), Cq.data_ptr(),
+                                           hn.data_ptr<float>(), (int)Cq.size(0), ip, assign.data_ptr<int>(),
+                                           md, m2, xhp, xmp, cur_stream()), "kmeans_assign_rows");
+}
+
+// the dense filtered iteration
+void kmeans_assign_filtered(const Tensor& X, const Tensor& Cq, const Tensor& hn,
+                            const std::optional<Tensor>& idx, int64_t m, Tensor assign,
+                            const Tensor& m_dev, const Tensor& tol, Tensor ul, Tensor changed,
+                            Tensor n_changed, const std::optional<Tensor>& a_prev,
+                            const std::optional<Tensor>& acl, const std::optional<Tensor>& chg_new,
+                            const std::optional<Tensor>& chg_old) {
+  const int32_t* ip = km_rows_check("kmeans_assign_filtered", X, Cq, hn, idx, m, assign);
+  const DalgoKmPost post = km_post_check("kmeans_assign_filtered", X, ip, m, m_dev, tol, ul, changed,
+                                         n_changed, a_prev, acl, chg_new, chg_old);
+  DeviceGuard guard(X.device());
+  DALGO_CHECK_HIP(dalgo_kmeans_assign_filtered(X.data_ptr(), m, X.stride(0), (int)Cq.size(1), Cq.data_ptr(),
+                                               hn.data_ptr<float>(), (int)Cq.size(0), ip,
+                                               assign.data_ptr<int>(), &post, cur_stream()), "kmeans_assign_filtered");
+}
+
+// the candidate-pruned filtered iteration: idx = the active rows sorted by cluster, tiles
+// int32 [T, 4]; ndb / dnb (+ tau_cap): the drift-aware lists; tile16: tiles of <= 384 rows,
+// 16x16x32 form
+void kmeans_assign_cand(const Tensor& X, const Tensor& Cq, const Tensor& hn, const Tensor& idx,
+                        int64_t m, Tensor assign, const Tensor& m_dev, const Tensor& tol, Tensor ul,
+                        Tensor changed, Tensor n_changed, const Tensor& tiles, const Tensor& n_tiles,
+                        const Tensor& hnb, const Tensor& nb, const Tensor& nd,
+                        const std::optional<Tensor>& ndb, const std::optional<Tensor>& dnb,
+                        const std::optional<Tensor>& tau_cap, bool extend, bool drift_ball,
+                        bool tile16, const std::optional<Tensor>& a_prev,
+                        const std::optional<Tensor>& acl, const std::optional<Tensor>& chg_new,
+                        const std::optional<Tensor>& chg_old) {
+  const int32_t* ip = km_rows_check("kmeans_assign_cand", X, Cq, hn, idx, m, assign);
+  const DalgoKmPost post = km_post_check("kmeans_assign_cand", X, ip, m, m_dev, tol, ul, changed,
+                                         n_changed, a_prev, acl, chg_new, chg_old);
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&tiles, &n_tiles, &hnb, &nb, &nd})
+    check_dev(*t, "cand");
+  TORCH_CHECK(tiles.scalar_type() == at::kInt && n_tiles.scalar_type() == at::kLong &&
+                  hnb.scalar_type() == at::kFloat && nb.scalar_type() == at::kInt &&
+                  nd.scalar_type() == at::kFloat,
+              "kmeans_assign_cand: cand dtypes");
+  const int64_t kpad = Cq.size(0), k = hnb.numel() / kpad;
+  TORCH_CHECK(kpad <= 1024 && k >= 1 && k <= kpad && nb.numel() >= k * kpad &&
+                  nd.numel() >= k * kpad && tiles.numel() % 4 == 0,
+              "kmeans_assign_cand: cand sizes (kpad <= 1024)");
   DalgoKmCand cd{};
-  const DalgoKmCand* cp = nullptr;
-  if (!cand.empty()) {
-    TORCH_CHECK((cand.size() == 5 || cand.size() == 7 || cand.size() == 8) && pp != nullptr && ip != nullptr,
-                "kmeans_assign_idx: cand = 5 (7, 8) tensors, with the device-count form and idx");
-    for (const Tensor& t : cand) check_dev(t, "cand");
-    TORCH_CHECK(cand[0].scalar_type() == at::kInt && cand[1].scalar_type() == at::kLong &&
-                    cand[2].scalar_type() == at::kFloat && cand[3].scalar_type() == at::kInt &&
-                    cand[4].scalar_type() == at::kFloat,
-                "kmeans_assign_idx: cand dtypes");
-    const int64_t k = cand[2].numel() / kpad;
-    TORCH_CHECK(kpad <= 1024 && k >= 1 && k <= kpad && cand[3].numel() >= k * kpad &&
-                    cand[4].numel() >= k * kpad && cand[0].numel() % 4 == 0,
-                "kmeans_assign_idx: cand sizes (kpad <= 1024)");
-    cd.tiles = cand[0].data_ptr<int32_t>();
-    cd.n_tiles = reinterpret_cast<const unsigned long long*>(cand[1].data_ptr<int64_t>());
-    cd.hnb = cand[2].data_ptr<float>();
-    cd.nb = cand[3].data_ptr<int32_t>();
-    cd.nd = cand[4].data_ptr<float>();
-    cd.extend = (cand_extend & 1) != 0;
-    cd.tile16 = (cand_extend & 2) != 0;   // bit 1: tiles of <= 384 rows, 16x16x32 form
-    cd.max_tiles = cand[0].numel() / 4;
-    if (cand.size() >= 7) {
-      TORCH_CHECK(cand[5].scalar_type() == at::kFloat && cand[6].scalar_type() == at::kFloat &&
-                      cand[5].numel() >= k * kpad && cand[6].numel() >= k * kpad,
-                  "kmeans_assign_idx: ndb / dnb f32 [k * kpad]");
-      cd.ndb = cand[5].data_ptr<float>();
-      cd.dnb = cand[6].data_ptr<float>();
-    }
-    if (cand.size() == 8) {
-      TORCH_CHECK(cand[7].scalar_type() == at::kFloat && cand[7].numel() >= 1, "kmeans_assign_idx: tau_cap f32[1]");
-      cd.tau_cap = cand[7].data_ptr<float>();
-    }
-    cp = &cd;
+  cd.tiles = tiles.data_ptr<int32_t>();
+  cd.n_tiles = reinterpret_cast<const unsigned long long*>(n_tiles.data_ptr<int64_t>());
+  cd.hnb = hnb.data_ptr<float>();
+  cd.nb = nb.data_ptr<int32_t>();
+  cd.nd = nd.data_ptr<float>();
+  cd.extend = extend;
+  cd.drift_ball = drift_ball;
+  cd.tile16 = tile16;
+  cd.max_tiles = tiles.numel() / 4;
+  TORCH_CHECK(ndb.has_value() == dnb.has_value() && (ndb.has_value() || !tau_cap.has_value()),
+              "kmeans_assign_cand: ndb and dnb together (tau_cap only with them)");
+  if (ndb.has_value()) {
+    check_dev(*ndb, "cand");
+    check_dev(*dnb, "cand");
+    TORCH_CHECK(ndb->scalar_type() == at::kFloat && dnb->scalar_type() == at::kFloat &&
+                    ndb->numel() >= k * kpad && dnb->numel() >= k * kpad,
+                "kmeans_assign_cand: ndb / dnb f32 [k * kpad]");
+    cd.ndb = ndb->data_ptr<float>();
+    cd.dnb = dnb->data_ptr<float>();
+  }
+  if (tau_cap.has_value()) {
+    check_dev(*tau_cap, "cand");
+    TORCH_CHECK(tau_cap->scalar_type() == at::kFloat && tau_cap->numel() >= 1,
+                "kmeans_assign_cand: tau_cap f32[1]");
+    cd.tau_cap = tau_cap->data_ptr<float>();
   }
   DeviceGuard guard(X.device());
-  DALGO_CHECK_HIP(dalgo_kmeans_assign_idx(X.data_ptr(), m, X.stride(0), DP, Cq.data_ptr(),
-                                          hn.data_ptr<float>(), (int)kpad, ip,
-                                          assign.data_ptr<int>(), md, m2, nullptr, 0, xhp, xmp, pp,
-                                          cp, cur_stream()),
-                  "kmeans_assign_idx");
+  DALGO_CHECK_HIP(dalgo_kmeans_assign_cand(X.data_ptr(), m, X.stride(0), (int)Cq.size(1), Cq.data_ptr(),
+                                           hn.data_ptr<float>(), (int)Cq.size(0), ip, assign.data_ptr<int>(),
+                                           &post, &cd, cur_stream()), "kmeans_assign_cand");
 }
 
 // candidate-pruned K2 preparation: active rows sorted by cluster + tile table
@@ -1867,12 +1907,17 @@ TORCH_LIBRARY(dalgo, m) {
   m.def("kmeans_centre_bounds(Tensor cnow, Tensor cprev, int k, int d, Tensor(a!) delta, "
         "Tensor(b!) s) -> ()");
   m.def("kmeans_qsum(Tensor assign, Tensor xh, int k, Tensor(a!) Q) -> ()");
-  m.def("kmeans_assign_idx(Tensor X, Tensor Cq, Tensor hn, Tensor? idx, int m, Tensor(a!) assign, "
-        "Tensor[] cand, "
-        "Tensor(b!)? mind=None, Tensor(c!)? mind2=None, Tensor(d!)? xh=None, Tensor(e!)? xmax=None, "
-        "Tensor? m_dev=None, Tensor? a_prev=None, Tensor? tol=None, Tensor(f!)? ul=None, "
-        "Tensor(h!)? changed=None, Tensor(i!)? n_changed=None, "
-        "Tensor(j!)? chg_new=None, Tensor(l!)? chg_old=None, int cand_extend=1, Tensor? acl=None) -> ()");
+  m.def("kmeans_assign_rows(Tensor X, Tensor Cq, Tensor hn, Tensor? idx, int m, Tensor(a!) assign, "
+        "Tensor(b!)? mind=None, Tensor(c!)? mind2=None, Tensor(d!)? xh=None, Tensor(e!)? xmax=None) -> ()");
+  m.def("kmeans_assign_filtered(Tensor X, Tensor Cq, Tensor hn, Tensor? idx, int m, Tensor(a!) assign, "
+        "Tensor m_dev, Tensor tol, Tensor(f!) ul, Tensor(h!) changed, Tensor(i!) n_changed, "
+        "Tensor? a_prev=None, Tensor? acl=None, Tensor(j!)? chg_new=None, Tensor(l!)? chg_old=None) -> ()");
+  m.def("kmeans_assign_cand(Tensor X, Tensor Cq, Tensor hn, Tensor idx, int m, Tensor(a!) assign, "
+        "Tensor m_dev, Tensor tol, Tensor(f!) ul, Tensor(h!) changed, Tensor(i!) n_changed, "
+        "Tensor tiles, Tensor n_tiles, Tensor hnb, Tensor nb, Tensor nd, Tensor? ndb=None, "
+        "Tensor? dnb=None, Tensor? tau_cap=None, bool extend=True, bool drift_ball=True, "
+        "bool tile16=False, Tensor? a_prev=None, Tensor? acl=None, Tensor(j!)? chg_new=None, "
+        "Tensor(l!)? chg_old=None) -> ()");
   m.def("kmeans_bounds_init(Tensor mind, Tensor mind2, Tensor xmax, int n, Tensor(a!) ul, "
         "Tensor(c!) tol) -> ()");
   m.def("kmeans_update(Tensor(a!) C, Tensor S, Tensor cnt, Tensor(b!) Cq, Tensor(c!) hn, "
@@ -2007,6 +2052,8 @@ TORCH_LIBRARY_IMPL(dalgo, CUDA, m) {
   m.impl("kmeans_centre_bounds", &kmeans_centre_bounds);
   m.impl("kmeans_bounds_init", &kmeans_bounds_init);
   m.impl("kmeans_qsum", &kmeans_qsum);
-  m.impl("kmeans_assign_idx", &kmeans_assign_idx);
+  m.impl("kmeans_assign_rows", &kmeans_assign_rows);
+  m.impl("kmeans_assign_filtered", &kmeans_assign_filtered);
+  m.impl("kmeans_assign_cand", &kmeans_assign_cand);
   m.impl("kmeans_accumulate_sorted", &kmeans_accumulate_sorted);   // dispatches on its output counter
 }

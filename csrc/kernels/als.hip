@@ -25,6 +25,7 @@
 // 100k x 50k x 64 (bench/als_bench.py, 1 x MI355X): 3.90 ms = 5.13 TB/s of R, against
 // 5.64 ms for torch.matmul(torch.matmul(R, F), Ginv) (hipBLASLt).
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <algorithm>
 
 namespace dalgo {

@@ -25,6 +25,7 @@
 // Columns of P are independent, so ranks partition the targets z: no
 // communication besides the int64 count all-reduce of the fixpoint test.
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <algorithm>
 
 namespace dalgo {

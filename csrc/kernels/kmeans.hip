@@ -2413,6 +2413,31 @@ static hipError_t launch_assign(int DP, const void* X, int64_t n, int64_t ldx, c
   }
 }
 
+// The pipelined form of the row-subset entry points (4-wave blocks, 128-centre chunks,
+// double-buffered) at DP 64 or 128; a...: the arguments of launch_assign_pipe.
+template <int PT, bool PF, bool TOP2, bool BND = false, bool CND = false, bool DRIFT = false, typename... A>
+static hipError_t launch_assign_rows_pipe(int DP, A... a) {
+  if (DP == 128) return launch_assign_pipe<128, 4, PT, 4, 2, 2, PF, TOP2, BND, CND, DRIFT>(a...);
+  if (DP == 64) return launch_assign_pipe<64, 4, PT, 4, 2, 2, PF, TOP2, BND, CND, DRIFT>(a...);
+  return hipErrorInvalidValue;
+}
+
+// The kernels' argument block of a filtered iteration (cand: the candidate-pruned form).
+static KmAux km_aux(const DalgoKmPost& post, const DalgoKmCand* cand) {
+  KmAux aux{};
+  aux.mcount = post.mcount; aux.a_prev = post.a_prev; aux.tol = post.tol;
+  aux.ul = reinterpret_cast<float2*>(post.ul); aux.changed = post.changed; aux.n_changed = post.n_changed;
+  aux.cap = post.cap; aux.chg_new = post.chg_new; aux.chg_old = post.chg_old; aux.acl = post.acl;
+  if (cand != nullptr) {
+    aux.tiles = reinterpret_cast<const int4*>(cand->tiles);
+    aux.n_tiles = cand->n_tiles; aux.hnb = cand->hnb;
+    aux.nb = cand->nb; aux.nd = cand->nd; aux.extend = cand->extend;
+    aux.ndb = cand->ndb; aux.dnb = cand->dnb; aux.tau_cap = cand->tau_cap;
+    aux.drift_ball = cand->drift_ball;
+  }
+  return aux;
+}
+
 template <typename T, int DP>
 static hipError_t launch_segsum_dp(const void* X, int64_t ldx, const int* perm, const int64_t* cs,
                                    const int64_t* ss, int k, int seg, int64_t max_segs, float* S,
@@ -2541,99 +2566,77 @@ hipError_t dalgo_kmeans_assign(const void* X, int is_bf16, int64_t n, int64_t ld
                  : launch_assign<float>(DP, X, n, ldx, Cq, hn, kpad, assign, mind, sse, sse_mask, st);
 }
 
-// K2 (pipelined form) over the rows idx[0, m) of X only (bound-filtered Lloyd iteration).
-// idx may be null (rows 0 .. m); mind2 non-null selects the top-2 form (second-best
+// K2 over the rows idx[0, m) of X only (idx null: rows 0 .. m), one entry point per form.
+// All return success without a launch for m <= 0 and need kpad % 128 == 0.
+// The pass with a host row count: mind2 non-null selects the top-2 form (second-best
 // distance per row, a lower bound for the bound filter); xh / xmax: 0.5|x|^2 per row and
-// its maximum (full pass). post != null: the filtered-iteration form -- the row count is
-// *post->mcount (device; m its upper bound), a resident grid walks the tiles and the
-// bound update (u, l, changed rows vs a_prev) is fused into the epilogue.
-hipError_t dalgo_kmeans_assign_idx(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
-                                   const float* hn, int kpad, const int32_t* idx, int* assign,
-                                   float* mind, float* mind2, double* sse, int sse_mask, float* xh,
-                                   unsigned* xmax, const DalgoKmPost* post, const DalgoKmCand* cand,
-                                   hipStream_t st) {
+// its maximum (full pass).
+hipError_t dalgo_kmeans_assign_rows(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
+                                    const float* hn, int kpad, const int32_t* idx, int* assign,
+                                    float* mind, float* mind2, float* xh, unsigned* xmax,
+                                    hipStream_t st) {
   if (m <= 0) return hipSuccess;
   if (kpad % 128 != 0) return hipErrorInvalidValue;
   KmAux aux{};
   aux.xh = xh;
   aux.xmax = xmax;
-  if (cand != nullptr && post == nullptr) return hipErrorInvalidValue;
-  if (post != nullptr) {
-    aux.mcount = post->mcount; aux.a_prev = post->a_prev; aux.tol = post->tol;
-    aux.ul = reinterpret_cast<float2*>(post->ul); aux.changed = post->changed; aux.n_changed = post->n_changed;
-    aux.cap = post->cap; aux.chg_new = post->chg_new; aux.chg_old = post->chg_old; aux.acl = post->acl;
-    if ((aux.chg_new == nullptr) != (aux.chg_old == nullptr)) return hipErrorInvalidValue;
-    if (cand != nullptr) {
-      // idx = the active rows sorted by cluster (dalgo_kmeans_sort_active)
-      aux.tiles = reinterpret_cast<const int4*>(cand->tiles);
-      aux.n_tiles = cand->n_tiles; aux.hnb = cand->hnb;
-      aux.nb = cand->nb; aux.nd = cand->nd; aux.extend = cand->extend;
-      aux.ndb = cand->ndb; aux.dnb = cand->dnb; aux.tau_cap = cand->tau_cap;
-      aux.drift_ball = cand->extend;   // (no extension chunks in the drift form)
-      if (cand->tile16) {
-        // the 16x16x32 tiling with the list prefix / the drift-compacted list (tiles of
-        // <= 384 rows)
-        if (DP != 128 || idx == nullptr) return hipErrorInvalidValue;
-        if (cand->ndb != nullptr)
-          return launch_assign16<true, true, true>(X, cand->max_tiles * 384, ldx, Cq, hn, kpad, assign, nullptr,
-                                                   sse, sse_mask, nullptr, nullptr, st, idx, aux);
-        return launch_assign16<true, true>(X, cand->max_tiles * 384, ldx, Cq, hn, kpad, assign, nullptr, sse,
-                                           sse_mask, nullptr, nullptr, st, idx, aux);
-      }
-      if (cand->ndb != nullptr) {   // drift-aware candidate lists
-        if (DP == 128)
-          return launch_assign_pipe<128, 4, 2, 4, 2, 2, false, true, true, true, true>(
-              X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-        if (DP == 64)
-          return launch_assign_pipe<64, 4, 2, 4, 2, 2, false, true, true, true, true>(
-              X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-        return hipErrorInvalidValue;
-      }
-      if (DP == 128)
-        return launch_assign_pipe<128, 4, 2, 4, 2, 2, false, true, true, true>(
-            X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-      if (DP == 64)
-        return launch_assign_pipe<64, 4, 2, 4, 2, 2, false, true, true, true>(
-            X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-      return hipErrorInvalidValue;
-    }
-#ifndef KM_XP_NO16
-    // the dense form of the filtered iteration: 16x16x32 MFMAs, top-2 keys, no pruning
-    if (DP == 128 && assign16_fits(kpad, true) && idx != nullptr)
-      return launch_assign16<true>(X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, nullptr, nullptr,
-                                   st, idx, aux);
-#endif
-    if (cand == nullptr && aux.a_prev == nullptr && aux.acl == nullptr && idx == nullptr)
-      return hipErrorInvalidValue;
-    // top-2: 2 point tiles per wave (3 would spill past 256 VGPRs in the tile loop)
-    if (DP == 128)
-      return launch_assign_pipe<128, 4, 2, 4, 2, 2, false, true, true>(
-          X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-    if (DP == 64)
-      return launch_assign_pipe<64, 4, 2, 4, 2, 2, false, true, true>(
-          X, m, ldx, Cq, hn, kpad, assign, nullptr, sse, sse_mask, st, idx, nullptr, aux);
-    return hipErrorInvalidValue;
-  }
-  if (mind2 != nullptr) {
-    if (DP == 128)
-      return launch_assign_pipe<128, 4, 2, 4, 2, 2, false, true>(
-          X, m, ldx, Cq, hn, kpad, assign, mind, sse, sse_mask, st, idx, mind2, aux);
-    if (DP == 64)
-      return launch_assign_pipe<64, 4, 2, 4, 2, 2, false, true>(
-          X, m, ldx, Cq, hn, kpad, assign, mind, sse, sse_mask, st, idx, mind2, aux);
-    return hipErrorInvalidValue;
-  }
+  // top-2: 2 point tiles per wave (3 would spill past 256 VGPRs in the tile loop)
+  if (mind2 != nullptr)
+    return launch_assign_rows_pipe<2, false, true>(DP, X, m, ldx, Cq, hn, kpad, assign, mind, nullptr, 0, st, idx,
+                                                   mind2, aux);
 #ifndef KM_XP_NO16
   if (DP == 128 && idx == nullptr && assign16_fits(kpad))
-    return launch_assign16<false>(X, m, ldx, Cq, hn, kpad, assign, mind, sse, sse_mask, aux.xh, aux.xmax, st);
+    return launch_assign16<false>(X, m, ldx, Cq, hn, kpad, assign, mind, nullptr, 0, xh, xmax, st);
 #endif
-  if (DP == 128)
-    return launch_assign_pipe<128, 4, 3, 4, 2, 2, true>(X, m, ldx, Cq, hn, kpad, assign, mind, sse,
-                                                        sse_mask, st, idx, nullptr, aux);
-  if (DP == 64)
-    return launch_assign_pipe<64, 4, 3, 4, 2, 2, true>(X, m, ldx, Cq, hn, kpad, assign, mind, sse,
-                                                       sse_mask, st, idx, nullptr, aux);
-  return hipErrorInvalidValue;
+  return launch_assign_rows_pipe<3, true, false>(DP, X, m, ldx, Cq, hn, kpad, assign, mind, nullptr, 0, st, idx,
+                                                 nullptr, aux);
+}
+
+// The dense filtered iteration: the row count is *post->mcount (device; m its upper
+// bound), a resident grid walks the tiles and the bound update (u, l, changed rows vs
+// a_prev / acl / assign) is fused into the epilogue.
+hipError_t dalgo_kmeans_assign_filtered(const void* X, int64_t m, int64_t ldx, int DP,
+                                        const void* Cq, const float* hn, int kpad,
+                                        const int32_t* idx, int* assign, const DalgoKmPost* post,
+                                        hipStream_t st) {
+  if (m <= 0) return hipSuccess;
+  if (kpad % 128 != 0 || post == nullptr) return hipErrorInvalidValue;
+  const KmAux aux = km_aux(*post, nullptr);
+  if ((aux.chg_new == nullptr) != (aux.chg_old == nullptr)) return hipErrorInvalidValue;
+#ifndef KM_XP_NO16
+  // 16x16x32 MFMAs, top-2 keys, no pruning
+  if (DP == 128 && assign16_fits(kpad, true) && idx != nullptr)
+    return launch_assign16<true>(X, m, ldx, Cq, hn, kpad, assign, nullptr, nullptr, 0, nullptr, nullptr, st, idx,
+                                 aux);
+#endif
+  if (aux.a_prev == nullptr && aux.acl == nullptr && idx == nullptr) return hipErrorInvalidValue;
+  return launch_assign_rows_pipe<2, false, true, true>(DP, X, m, ldx, Cq, hn, kpad, assign, nullptr, nullptr, 0, st,
+                                                       idx, nullptr, aux);
+}
+
+// The candidate-pruned filtered iteration: idx = the active rows sorted by cluster
+// (dalgo_kmeans_sort_active); cand->ndb selects the drift-aware lists, cand->tile16 the
+// 16x16x32 tiling (tiles of <= 384 rows) with the list prefix / the drift-compacted list.
+hipError_t dalgo_kmeans_assign_cand(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
+                                    const float* hn, int kpad, const int32_t* idx, int* assign,
+                                    const DalgoKmPost* post, const DalgoKmCand* cand,
+                                    hipStream_t st) {
+  if (m <= 0) return hipSuccess;
+  if (kpad % 128 != 0 || post == nullptr || cand == nullptr) return hipErrorInvalidValue;
+  const KmAux aux = km_aux(*post, cand);
+  if ((aux.chg_new == nullptr) != (aux.chg_old == nullptr)) return hipErrorInvalidValue;
+  const bool drift = cand->ndb != nullptr;
+  if (cand->tile16) {
+    if (DP != 128 || idx == nullptr) return hipErrorInvalidValue;
+    const int64_t n = cand->max_tiles * 384;   // one block per slot of the tile table
+    auto* launch = drift ? launch_assign16<true, true, true> : launch_assign16<true, true>;
+    return launch(X, n, ldx, Cq, hn, kpad, assign, nullptr, nullptr, 0, nullptr, nullptr, st, idx, aux);
+  }
+  if (drift)
+    return launch_assign_rows_pipe<2, false, true, true, true, true>(DP, X, m, ldx, Cq, hn, kpad, assign, nullptr,
+                                                                     nullptr, 0, st, idx, nullptr, aux);
+  return launch_assign_rows_pipe<2, false, true, true, true>(DP, X, m, ldx, Cq, hn, kpad, assign, nullptr, nullptr,
+                                                             0, st, idx, nullptr, aux);
 }
 
 hipError_t dalgo_kmeans_update(float* C, const float* S, const unsigned long long* cnt, int k,

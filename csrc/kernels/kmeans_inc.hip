@@ -23,6 +23,7 @@
 // Every count (changed rows, active rows) stays on the device: the launches that
 // consume it read it there, so an iteration needs no host sync.
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 
 namespace dalgo {
 namespace {

@@ -24,6 +24,7 @@
 // destination is present after an iteration iff it received >= 1 record.
 // "standard" semantics: every vertex present, dangling mass redistributed.
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <algorithm>
 
 namespace dalgo {

@@ -7,6 +7,7 @@
 //     3 points (21-bit coordinates) per Philox block, count x^2+y^2 <= 1. VALU-bound;
 //     wave reduce (permlane swaps + DPP) -> one 64-bit atomic per block.
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <algorithm>
 
 namespace dalgo {

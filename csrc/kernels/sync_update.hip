@@ -12,6 +12,7 @@
 // local models) — launch-bound, so everything per step is fused into a single
 // grid and every rank applies the identical rule to replicated state (no driver).
 #include "dalgo/common.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <algorithm>
 
 namespace dalgo {

@@ -31,6 +31,7 @@
 // appended keys are plain stores read by the NEXT launch (kernel boundary).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 
 namespace dalgo {
 namespace {

@@ -22,6 +22,7 @@
 // only ever increase, so flags need no reset. The wait is bounded (wall clock):
 // on timeout the kernel sets *err and finishes, never hangs the GPU.
 #include "dalgo/xgmi.h"
+#include "launchers.h"   // the extern "C" entry point is checked against its declaration
 #include <cstring>
 
 namespace dalgo {

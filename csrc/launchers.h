@@ -31,8 +31,9 @@ struct DalgoLrTail {
   int pool_shift;
 };
 
-// Filtered k-means iteration (kmeans.hip dalgo_kmeans_assign_idx): the K2 epilogue
-// updates the Hamerly bounds and collects the rows whose cluster changed
+// Filtered k-means iteration (kmeans.hip dalgo_kmeans_assign_filtered and
+// dalgo_kmeans_assign_cand): the K2 epilogue updates the Hamerly bounds and collects the
+// rows whose cluster changed
 struct DalgoKmPost {
   const unsigned long long* mcount;   // active rows (device, written by km_filter)
   const int* a_prev;                  // their cluster before this iteration
@@ -46,17 +47,19 @@ struct DalgoKmPost {
   const int* acl;                     // optional: previous cluster of active row p (idx order)
 };
 
-// candidate-pruned K2 (dalgo_kmeans_sort_active + dalgo_km_centre_nbrs outputs)
+// candidate-pruned K2 (kmeans.hip dalgo_kmeans_assign_cand): the outputs of
+// dalgo_kmeans_sort_active + dalgo_km_centre_nbrs
 struct DalgoKmCand {
   const int32_t* tiles;               // [T][4]: cluster, first, end position, -
   const unsigned long long* n_tiles;
   const float* hnb;
   const int32_t* nb;
   const float* nd;
-  int extend;                         // stream extra chunks for tight lower bounds
+  int extend;                         // plain lists: stream extra chunks for tight lower bounds
   const float* ndb;                   // nullable: drift-aware lists (nd aligned with nb)
   const float* dnb;                   //           and each entry's centre shift
   const float* tau_cap;               // nullable (device): cap of the drift threshold
+  int drift_ball;                     // drift-aware lists: also drop the centres outside the ball
   int tile16;                         // tiles of <= 384 rows for the 16x16x32 form (CND)
   int64_t max_tiles;                  // capacity of the tile table (its launch grid)
 };
@@ -113,6 +116,30 @@ hipError_t dalgo_kmeans_accumulate_sorted(const void* X, int is_bf16, int64_t n,
 hipError_t dalgo_kmeans_update(float* C, const float* S, const unsigned long long* cnt, int k,
                                int d, int DP, void* Cq, int is_bf16, float* hn, int kpad,
                                float* shift2, hipStream_t st);
+// K2 over a row subset, one entry point per form. Common arguments: bf16 points X (row
+// stride ldx), m rows (the host's upper bound where the count is on the device), DP 64 or
+// 128, centres Cq / hn [kpad], kpad % 128 == 0, idx nullable (rows 0 .. m).
+// The pass with a host row count (mind2: the top-2 form; xh / xmax: 0.5|x|^2 and its max).
+hipError_t dalgo_kmeans_assign_rows(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
+                                    const float* hn, int kpad, const int32_t* idx, int* assign,
+                                    float* mind, float* mind2, float* xh, unsigned* xmax,
+                                    hipStream_t st);
+// The dense filtered iteration: *post->mcount rows, bound update fused into the epilogue.
+hipError_t dalgo_kmeans_assign_filtered(const void* X, int64_t m, int64_t ldx, int DP,
+                                        const void* Cq, const float* hn, int kpad,
+                                        const int32_t* idx, int* assign, const DalgoKmPost* post,
+                                        hipStream_t st);
+// The candidate-pruned filtered iteration: idx = the active rows sorted by cluster.
+hipError_t dalgo_kmeans_assign_cand(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
+                                    const float* hn, int kpad, const int32_t* idx, int* assign,
+                                    const DalgoKmPost* post, const DalgoKmCand* cand,
+                                    hipStream_t st);
+hipError_t dalgo_kmeans_sort_active(const int32_t* acl, const int32_t* idx, int64_t cap,
+                                    const unsigned long long* n_active, int k, int B, int64_t chunk,
+                                    int* block_counts, int64_t* cstart, int64_t* seg_start,
+                                    int32_t* rows_sorted, int tile, int32_t* tiles,
+                                    unsigned long long* n_tiles,
+                                    int64_t max_tiles, hipStream_t st);
 
 // ---- K4 PageRank + R-MAT generator (pagerank.hip)
 hipError_t dalgo_rmat(uint64_t seed, int scale, int64_t e_off, int64_t n, float a, float b, float c,
@@ -139,7 +166,6 @@ hipError_t dalgo_pr_update(const float* acc, const int32_t* pres, const int32_t*
                            float q, float invN, int mode, const float* dangling_in, float* r,
                            float* c, float* dangling_out, hipStream_t st);
 
-// ---- K9 transitive closure (closure.hip)
 // ---- K3 incremental form (kmeans_inc.hip)
 hipError_t dalgo_km_diff(const int32_t* a_new, const int32_t* a_old, int64_t n, int32_t* changed,
                          unsigned long long* n_changed, int64_t cap, hipStream_t st);
@@ -151,17 +177,6 @@ hipError_t dalgo_km_centre_bounds(const void* cnow, const void* cprev, int is_bf
                                   int DP, float* delta, float* s, hipStream_t st);
 hipError_t dalgo_km_qsum(const int32_t* assign, const float* xh, int64_t n, int k, double* Q,
                          hipStream_t st);
-hipError_t dalgo_kmeans_assign_idx(const void* X, int64_t m, int64_t ldx, int DP, const void* Cq,
-                                   const float* hn, int kpad, const int32_t* idx, int* assign,
-                                   float* mind, float* mind2, double* sse, int sse_mask, float* xh,
-                                   unsigned* xmax, const DalgoKmPost* post,
-                                   const DalgoKmCand* cand, hipStream_t st);
-hipError_t dalgo_kmeans_sort_active(const int32_t* acl, const int32_t* idx, int64_t cap,
-                                    const unsigned long long* n_active, int k, int B, int64_t chunk,
-                                    int* block_counts, int64_t* cstart, int64_t* seg_start,
-                                    int32_t* rows_sorted, int tile, int32_t* tiles,
-                                    unsigned long long* n_tiles,
-                                    int64_t max_tiles, hipStream_t st);
 hipError_t dalgo_km_centre_nbrs(const void* cq, const void* cprev, const float* hn, int k, int kpad,
                                 int d, int DP, float* delta, float* s, float* nd, int32_t* nb,
                                 float* hnb, float* ndb, float* dnb, hipStream_t st);
@@ -179,6 +194,8 @@ hipError_t dalgo_tcs_expand(const uint64_t* fkeys, int64_t nd, const int64_t* ex
 hipError_t dalgo_tcs_insert(const uint64_t* src, int64_t n, uint64_t* table, uint64_t mask,
                             int append, uint64_t* keys, unsigned long long* n_keys, uint64_t cap,
                             unsigned* err, hipStream_t st);
+
+// ---- K9 transitive closure (closure.hip)
 hipError_t dalgo_tc_step(const void* A, int64_t lda, const void* Told, void* Tnew, int64_t ldt,
                          int npad, int nz, int variant, unsigned long long* count, hipStream_t st);
 

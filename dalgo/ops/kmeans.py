@@ -283,10 +283,6 @@ class CandWorkspace:
         self.tiles = torch.empty(tiles * 4, **i32)      # (cluster, first, end, -) per tile
         self.n_tiles = torch.zeros(1, **i64)
 
-    def cand(self):
-        c = [self.tiles, self.n_tiles, self.hnb, self.nb, self.nd]
-        return c + [self.ndb, self.dnb, self.tau_cap] if self.ndb is not None else c
-
 
 def centre_nbrs(cen: Centers, Cq_prev: torch.Tensor, delta: torch.Tensor, s: torch.Tensor,
                 ws: CandWorkspace):
@@ -362,17 +358,22 @@ def assign_rows(X: torch.Tensor, cen: Centers, idx: torch.Tensor | None, m: int,
     farther than c_a from every tile point (l bounds the distances to the previous
     centres); the kept entries are compacted in the tile prologue, the dropped ones bound
     the new l by l - (their largest shift), and no extension chunks are streamed."""
+    rows = dict(X=X, Cq=cen.Cq, hn=cen.hn, idx=idx, m=int(m), assign=assign)
     if post is None:
-        _ext.ops().kmeans_assign_idx(X, cen.Cq, cen.hn, idx, int(m), assign, [], mind, mind2, xh,
-                                     xmax)
+        _ext.ops().kmeans_assign_rows(**rows, mind=mind, mind2=mind2, xh=xh, xmax=xmax)
         return
-    _ext.ops().kmeans_assign_idx(X, cen.Cq, cen.hn, idx, int(m), assign,
-                                 cand.cand() if cand is not None else [], None, None, None, None,
-                                 post["m_dev"], post.get("a_prev"), post["tol"], post["ul"],
-                                 post["changed"], post["n_changed"],
-                                 post.get("chg_new"), post.get("chg_old"),
-                                 int(bool(extend)) | (2 if cand is not None and cand.tile == CAND16_TILE else 0),
-                                 post.get("acl"))
+    rows.update(m_dev=post["m_dev"], tol=post["tol"], ul=post["ul"], changed=post["changed"],
+                n_changed=post["n_changed"], a_prev=post.get("a_prev"), acl=post.get("acl"),
+                chg_new=post.get("chg_new"), chg_old=post.get("chg_old"))
+    if cand is None:
+        _ext.ops().kmeans_assign_filtered(**rows)
+        return
+    # ``extend`` carries both switches: plain lists read it as extend, drift-aware lists as
+    # "also drop the centres outside the ball" (the model passes drift_ball() there)
+    _ext.ops().kmeans_assign_cand(**rows, tiles=cand.tiles, n_tiles=cand.n_tiles, hnb=cand.hnb,
+                                  nb=cand.nb, nd=cand.nd, ndb=cand.ndb, dnb=cand.dnb,
+                                  tau_cap=cand.tau_cap, extend=bool(extend),
+                                  drift_ball=bool(extend), tile16=cand.tile == CAND16_TILE)
 
 
 def bounds_init(mind: torch.Tensor, mind2: torch.Tensor, xmax: torch.Tensor, n: int,

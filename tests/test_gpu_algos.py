@@ -1205,3 +1205,69 @@ def test_kmeans_assign_rows_drift_candidates(cuda, d, tile16):
     exp = torch.nonzero(sel & (a != a_prev))[:, 0]
     assert c == exp.numel()
     assert torch.equal(torch.sort(changed[:c]).values.long(), exp)
+
+
+def test_kmeans_assign_ops_reject_before_launch(cuda):
+    """The three row-subset K2 ops (kmeans_assign_rows / _filtered / _cand) refuse a
+    malformed call in their host-side checks -- a TORCH_CHECK of the op, or the launcher's
+    invalid-value return -- before any launch: assign, ul and the changed count stay as
+    they were. m = 0 returns without an error and without a write. (The device counts are
+    zero as well, so a launch that slipped through would find no rows and no tiles.)"""
+    from dalgo.ops import _ext
+    ops = _ext.ops()
+    n = 384
+    i32 = dict(dtype=torch.int32, device=cuda)
+    i64 = dict(dtype=torch.int64, device=cuda)
+
+    def case(d, kpad=128, drift=False):
+        Cq = torch.randn(kpad, d, device=cuda).to(torch.bfloat16)
+        rows = dict(X=torch.randn(n, d, device=cuda).to(torch.bfloat16), Cq=Cq,
+                    hn=0.5 * Cq.float().square().sum(1), idx=torch.arange(n, **i32), m=n,
+                    assign=torch.full((n,), -7, **i32))
+        post = dict(m_dev=torch.zeros(1, **i64), tol=torch.zeros(1, device=cuda),
+                    ul=torch.ones(n, 2, device=cuda), changed=torch.empty(n, **i32),
+                    n_changed=torch.zeros(1, **i64))
+        ws = K.CandWorkspace(cuda, n, kpad, kpad, d, drift=drift, tile=K.CAND16_TILE)
+        cand = dict(tiles=ws.tiles.zero_(), n_tiles=ws.n_tiles, hnb=ws.hnb.zero_(), nb=ws.nb.zero_(),
+                    nd=ws.nd.zero_(), tile16=True)
+        if drift:
+            cand.update(ndb=ws.ndb.zero_(), dnb=ws.dnb.zero_(), tau_cap=ws.tau_cap)
+        return rows, post, cand
+
+    def untouched(rows, post):
+        assert bool((rows["assign"] == -7).all())
+        assert bool((post["ul"] == 1).all()) and int(post["n_changed"].item()) == 0
+
+    def rejected(why, op, rows, post, **kw):
+        with pytest.raises(RuntimeError, match=why):
+            op(**rows, **kw)
+        untouched(rows, post)
+
+    mind = torch.zeros(n, device=cuda)
+    # the 16x16x32 tiling exists at DP 128 only (the launcher's invalid-value return)
+    rows, post, cand = case(64)
+    rejected("kmeans_assign_cand launch failed", ops.kmeans_assign_cand, rows, post, **post, **cand)
+    rows, post, cand = case(128, drift=True)
+    del cand["dnb"]
+    rejected("ndb and dnb together", ops.kmeans_assign_cand, rows, post, **post, **cand)
+    rows, post, cand = case(128)
+    rejected("chg_new and chg_old together", ops.kmeans_assign_filtered, rows, post, **post,
+             chg_new=torch.empty(n, **i32))
+    rejected("kmeans_assign_rows: mind", ops.kmeans_assign_rows, rows, post)
+    rejected("kmeans_assign_rows: mind", ops.kmeans_assign_rows, rows, post, mind2=mind)
+    # m = 0: nothing to do, in every form and in both candidate tilings
+    none = dict(rows, m=0)
+    ops.kmeans_assign_rows(**none, mind=mind)
+    ops.kmeans_assign_rows(**none, mind=mind, mind2=torch.zeros(n, device=cuda))
+    ops.kmeans_assign_filtered(**none, **post)
+    ops.kmeans_assign_cand(**none, **post, **cand)
+    ops.kmeans_assign_cand(**none, **post, **dict(cand, tile16=False))
+    untouched(rows, post)
+    assert bool((mind == 0).all())
+    rows, post, cand = case(128, kpad=1152)
+    rejected("kpad <= 1024", ops.kmeans_assign_cand, rows, post, **post, **cand)
+    rejected("kpad <= 1024", ops.kmeans_assign_cand, rows, post, **post, **dict(cand, tile16=False))
+    rows, post, cand = case(128, kpad=96)
+    rejected("kmeans_assign_rows: kpad % 128", ops.kmeans_assign_rows, rows, post, mind=mind)
+    rejected("kmeans_assign_filtered: kpad % 128", ops.kmeans_assign_filtered, rows, post, **post)
+    rejected("kmeans_assign_cand: kpad % 128", ops.kmeans_assign_cand, rows, post, **post, **cand)
